@@ -6,7 +6,7 @@ A "step" is one full shard proof per GPU — MachineProver::commit + open (crate
 shapes them (the executor's shape check closes the shard, `CoreShapeConfig::fix_shape` pads it: ziren_amd/shape.py) at SHARD_SIZE = 2^21 —
 1 569 808 cycles in a Cpu trace of 2^22 rows, 16 core chips + Byte + Program.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 ONE experiment for every N (the 1 -> N curve compares like with like): one process per GPU (launched by the driver through
 torch.distributed.run, or by this script itself when WORLD_SIZE is not set: `python bench.py --gpus 8` starts 8 ranks); K N distinct
@@ -16,12 +16,15 @@ proof, the next shard's events crossing PCIe under the current proof; the proof 
 no-op at N = 1); there is no data-path collective. Per-GPU work is fixed: scaling is weak, value = shards / max-over-ranks time. Every
 lane starts the timed region with its first shard's events resident in HBM (claimed and prefetched before the barrier).
 
-After the timed region (outside `value`) rank 0 runs the resident one-lane leg on the same shard — traces resident in HBM, one shard in
-flight — for the per-kernel figures: `roofline` (dominant kernel, HIP events), `valu`, `lde`, `kernels_ms` (a pass with the side-stream
-overlap off, so that the durations add up), `resident_one_lane`; and, at N = 1, the continuity legs and `cpu_baseline`.
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the last step's proofs if `--dump-outputs DIR`
+is given, print the line (`verified` is null: nothing was checked). `--full` adds everything else, all of it after the timed region and
+outside `value`: the gathered proofs through the restated verifier (oracle verify_shard); then rank 0 runs the resident one-lane leg on the
+same shard — traces resident in HBM, one shard in flight — for the per-kernel figures: `roofline` (dominant kernel, HIP events), `valu`,
+`lde`, `kernels_ms` (a pass with the side-stream overlap off, so that the durations add up), `resident_one_lane`; and, at N = 1, the
+continuity legs and `cpu_baseline`.
 
-Every number this file prints belongs to proofs the restated verifier (oracle verify_shard, outside the timed region) accepted: a leg
-whose proof is rejected raises instead of printing. `--resident` prints the old resident-only line (profiling scripts use it).
+Under `--full` every number this file prints belongs to proofs the restated verifier accepted: a leg whose proof is rejected raises
+instead of printing. `--resident` prints the old resident-only line (profiling scripts use it).
 """
 import argparse
 import ctypes as C
@@ -258,6 +261,22 @@ def verify_or_die(wl, fri, ch0, proof, what):
     if rc != 0:
         raise SystemExit(f"bench.py: the verifier REJECTED the {what} proof (code {rc}); nothing is reported for it")
     return True
+
+
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (proof words are below 2^32, so the values are exact). Should the arrays
+    hold more than DUMP_BYTES, each keeps a fixed, seeded sample of its words, in order."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(np.asarray(a).size for a in arrays.values()) * 8
+    rng = np.random.default_rng(0x5A4B)
+    for name, a in arrays.items():
+        a = np.asarray(a).ravel()
+        if total > DUMP_BYTES:
+            a = a[np.sort(rng.choice(a.size, size=max(1, a.size * DUMP_BYTES // total), replace=False))]
+        np.save(os.path.join(dirname, f"{name}.npy"), a.astype(np.float64))
 
 
 # ---- legs --------------------------------------------------------------------------------------------------------------------------------
@@ -773,15 +792,19 @@ def farm_main(args, farm, fri, built):
     cpu_per_shard_max = farm.max_over_ranks(cpu_per_shard)
     proved = farm.sum_over_ranks(float(len(ids)))
     fewest = -farm.max_over_ranks(-float(len(ids)))
-    # verification, outside the timed region. N = 1: EVERY gathered proof goes through the restated verifier (a fraction of a second each on
-    # the box's cores). N > 1: every lane's last proof on every rank — each context's transcript is checked, bounded at M proofs per rank
-    # (seconds on a rank's share of the host cores) — and `verified_proofs` says exactly how many of how many that was.
+    # the last step's outputs: the proof streams of the last shard of every GPU (of the queue's last shard with --queue), in shard order
+    if args.dump_outputs and rank == 0:
+        last = range(n_shards - (1 if args.queue > 0 else world), n_shards)
+        dump_outputs(args.dump_outputs, {f"proof_shard{i:05d}": gathered[i] for i in last})
+    # --full: verification, outside the timed region. N = 1: EVERY gathered proof goes through the restated verifier (a fraction of a second
+    # each on the box's cores). N > 1: every lane's last proof on every rank — each context's transcript is checked, bounded at M proofs per
+    # rank (seconds on a rank's share of the host cores) — and `verified_proofs` says exactly how many of how many that was.
     ok, checked = 1.0, 0
-    if world == 1 and gathered is not None:
+    if args.full and world == 1 and gathered is not None:
         for i, p in enumerate(gathered):
             ok = min(ok, 1.0 if lane.verify(i, p) else 0.0)
             checked += 1
-    else:
+    elif args.full:
         for l in lanes:
             if l.last is not None:
                 ok = min(ok, 1.0 if l.verify_last() else 0.0)
@@ -803,9 +826,10 @@ def farm_main(args, farm, fri, built):
             "steps": n_shards if args.queue > 0 else per_gpu, "shards": n_shards,
             "warmup": warm, "ms_per_step": round(ms if args.queue > 0 else elapsed / per_gpu * 1e3, 3), "ms_per_shard": round(ms, 3),
             "higher_is_better": True, "scaling": "strong" if args.queue > 0 else "weak",
-            "vs_baseline": None, "dtype": "u32", "verified": True, "verified_proofs": {"checked_by_the_verifier": verified_proofs, "of": n_shards,
-                                                                                    "which": "every gathered proof" if world == 1 else "the last proof of every lane of every rank",
-                                                                                    "all_gathered_streams_distinct": True},
+            "vs_baseline": None, "dtype": "u32", "verified": True if args.full else None,
+            "verified_proofs": {"checked_by_the_verifier": verified_proofs, "of": n_shards,
+                                "which": "every gathered proof" if world == 1 else "the last proof of every lane of every rank",
+                                "all_gathered_streams_distinct": True} if args.full else None,
             "stub": stub or None,
             "data": f"synthetic (the fibonacci guest's events in closed form, ziren_amd/fibfast.py; no executor or ELF in this environment; {pool_n} distinct middle shards of the guest per rank, their events page-locked)",
             "config": {"workload": (f"FIB-S{args.shard_size_log}: {n_shards} shard proofs ({'as given' if args.queue > 0 else str(per_gpu) + ' per GPU'}), each its own transcript, over {pool_n} distinct event sets per rank "
@@ -828,7 +852,7 @@ def farm_main(args, farm, fri, built):
             "event_bytes_per_shard": lane.event_bytes,
             "h2d_GBps_per_rank": round(lane.event_bytes * len(ids) / elapsed / 1e9, 2),      # rank 0's events over the timed region: what its PCIe link carried
             "shards_proved": int(proved), "shards_proved_by_rank0": len(ids), "fewest_shards_on_a_rank": int(fewest), "lib_digest": lib_digest})
-    if rank == 0 and not stub:
+    if rank == 0 and not stub and args.full:
         farm_extras(args, fri, lane, lanes, line, world, elapsed, n_shards)
     t_post = time.perf_counter()
     if rank == 0:
@@ -987,7 +1011,13 @@ def main():
     ap.add_argument("--inflight", type=int, default=2, help="shards in flight per GPU (a context + host thread each); 2 fills one proof's transcript "
                     "round trips and launch gaps with the other's kernels")
     ap.add_argument("--queue", type=int, default=0, metavar="SHARDS", help="deal SHARDS distinct shards in all through the claim queue (strong scaling) instead of --steps per GPU")
+    ap.add_argument("--full", action="store_true", help="after the timed region: verify the proofs, then the resident leg's per-kernel figures, the continuity, reduce and "
+                    "micro legs and the CPU baseline (the --no-* options trim these); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's proof streams as DIR/proof_shard<id>.npy (float64, "
+                    "the words exactly); --resident: DIR/proof.npy")
     args = ap.parse_args()
+    if args.dump_outputs and (args.tracegen or args.workload == "reduce-tree"):
+        raise SystemExit("bench.py: --dump-outputs is for the shard-proof line (and --resident)")
     if args.log_rows is None:
         args.log_rows = 21 if (args.workload == "fib-tight" or args.tracegen) else 22
     if args.tracegen:
@@ -1114,6 +1144,8 @@ def resident_main(args, farm, fri):
     hp, pk, ch0 = wl.setup(ctx, fri, not args.interpreter)
     traces = wl.resident_traces(ctx)            # inputs resident in HBM before timing
     leg = resident_leg(farm, wl, hp, pk, ch0, traces, args.steps, args.warmup, args.kernel_timing)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"proof": leg["proof"]})
     verify_or_die(wl, fri, ch0, leg["proof"], wl.tag)
     steps = args.steps
     ms_per_step = leg["elapsed"] / steps * 1e3

@@ -17,7 +17,7 @@ def _run(args, env_extra, timeout=240):
 
 
 def test_gpus_2_without_a_launcher_starts_two_ranks_and_prints_one_line():
-    r = _run(["--gpus", "2"], {"ZKM_BENCH_STUB_PROVER": "1"})
+    r = _run(["--gpus", "2", "--full"], {"ZKM_BENCH_STUB_PROVER": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -33,7 +33,7 @@ def test_n1_and_n2_lines_are_one_experiment_with_the_same_keys():
     shards in flight per GPU, --steps shards per GPU — so value(N) / (N value(1)) compares like with like."""
     lines = {}
     for n in (1, 2):
-        r = _run(["--gpus", str(n), "--steps", "6", "--warmup", "1"], {"ZKM_BENCH_STUB_PROVER": "1"})
+        r = _run(["--gpus", str(n), "--steps", "6", "--warmup", "1", "--full"], {"ZKM_BENCH_STUB_PROVER": "1"})
         assert r.returncode == 0, r.stderr[-2000:]
         out = [l for l in r.stdout.splitlines() if l.strip()]
         assert len(out) == 1, r.stdout
@@ -58,6 +58,24 @@ def test_steps_means_exactly_that_many_shards_per_gpu():
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["steps"] == 1 and line["shards"] == 1 and line["shards_proved"] == 1
+
+
+def test_a_plain_run_times_the_steps_and_dumps_the_last_steps_proofs(tmp_path):
+    """Without --full nothing but the timed steps runs after the warm-up (`verified` null: no proof was checked); --dump-outputs writes
+    the last step's proof stream — of the last shard at N = 1 — as float64 words, the same on every run with the same arguments."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], {"ZKM_BENCH_STUB_PROVER": "1"})
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["shards_proved"] == 3 and line["ms_per_step"] > 0
+        assert line["verified"] is None and line["verified_proofs"] is None and line["cpu_baseline"] is None
+        assert sorted(os.listdir(d)) == ["proof_shard00002.npy"]
+        dumps.append(np.load(d / "proof_shard00002.npy"))
+    assert dumps[0].dtype == np.float64 and np.array_equal(dumps[0], dumps[1])
+    assert dumps[0].tolist() == [0x5AFE, 2, 0] + [2] * 10          # StubLane's stream for shard 2 on rank 0
 
 
 def test_gpus_must_agree_with_the_process_group():

@@ -7,21 +7,21 @@ import pytest
 
 from ziren_amd import fibfast, shape as SH
 
-REF = "/root/reference/crates/core/machine/src/shape/maximal_shapes.json"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_the_committed_table_is_the_reference_s():
-    """Every maximal shape of the reference's JSON, chip for chip (runs where /root/reference exists; the GPU box has only the fixture)."""
-    if not os.path.exists(REF):
-        pytest.skip("no /root/reference here")
-    src = json.load(open(REF))
-    assert sorted(int(k) for k in src) == SH.registered_sizes()
-    for key, lst in src.items():
-        mine = SH.maximal_shapes(int(key))
-        assert len(mine) == len(lst)
-        for a, b in zip(mine, lst):
-            assert a == b["inner"]
-    costs = json.load(open("/root/reference/crates/core/executor/src/artifacts/mips_costs.json"))
+    """Every maximal shape of the reference's JSON, chip for chip: the committed table in canonical form has the digest, sizes and counts
+    tests/golden/gen_reference_tables.py recorded from the reference's maximal_shapes.json; the costs are its mips_costs.json."""
+    import sys
+    sys.path.insert(0, GOLDEN)
+    import gen_reference_tables as G
+    want = json.load(open(os.path.join(GOLDEN, "reference_tables.json")))["core_maximal_shapes"]
+    assert SH.registered_sizes() == want["sizes"]
+    mine = {str(k): SH.maximal_shapes(k) for k in SH.registered_sizes()}
+    assert {k: len(v) for k, v in mine.items()} == want["counts"]
+    assert G.canonical_shapes(mine) == want["sha256"]
+    costs = json.load(open(os.path.join(GOLDEN, "mips_costs.json")))["costs"]
     assert SH.costs() == costs
 
 

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 run() {
   local L=$1; shift
   for rep in 1 2; do
-    env "$@" python bench.py --no-extra --no-cpu-baseline --steps 10 --warmup 2 2>/dev/null | python -c "
+    env "$@" python bench.py --full --no-extra --no-cpu-baseline --steps 10 --warmup 2 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); p=l['phases_ms']
 print('$L rep $rep: step %.3f ms  commit main %.3f  commit perm %.3f  commit quotient %.3f  FRI commit phase %.3f  verified %s' % (l['ms_per_step'], p['commit main'], p['commit permutation'], p['commit quotient'], p['open: FRI commit phase'], l['verified']))"

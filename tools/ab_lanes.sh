@@ -6,7 +6,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 run() {
   local L=$1; shift
-  env "$@" python bench.py --steps 20 --warmup 3 --no-extra --no-cpu-baseline 2>/dev/null | python -c "
+  env "$@" python bench.py --full --steps 20 --warmup 3 --no-extra --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); k=l['kernels_ms']
 print('$L: two lanes from events %.3f ms/shard   resident one lane %.3f ms   quotient %.3f  eval_columns %.3f  cpu s/shard %.3f  verified %s' % (l['ms_per_shard'], l['resident_one_lane']['ms_per_step'], k['quotient']['ms'], k['eval_columns']['ms'], l['host_cpu_s_per_shard']['rank0'], l['verified']))"

@@ -6,7 +6,7 @@ import json,sys; l=json.loads(sys.stdin.read()); print('%-34s %.3f ms/shard  hos
 for rep in 1 2 3; do
   for q in 16 4; do
     for ov in 1 0; do
-      GPU_MAX_HW_QUEUES=$q ZKM_LDE_OVERLAP=$ov python bench.py --steps 40 --warmup 3 --no-extra --no-cpu-baseline 2>/dev/null | show "queues=$q side-stream overlap $ov"
+      GPU_MAX_HW_QUEUES=$q ZKM_LDE_OVERLAP=$ov python bench.py --full --steps 40 --warmup 3 --no-extra --no-cpu-baseline 2>/dev/null | show "queues=$q side-stream overlap $ov"
     done
   done
 done

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 run() {
   local L=$1; shift
   for rep in 1 2; do
-    env "$@" python bench.py --no-extra --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | python -c "
+    env "$@" python bench.py --full --no-extra --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); k=l['kernels_ms']
 print('$L rep $rep: step %.3f ms  perm_rows %.3f ms (%d launches)  quotient %.3f  verified %s' % (l['ms_per_step'], k['perm_rows']['ms'], k['perm_rows']['launches'], k['quotient']['ms'], l['verified']))"

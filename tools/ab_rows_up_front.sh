@@ -6,7 +6,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R
 run() {
   local L=$1; shift
-  env "$@" python bench.py --no-extra --no-cpu-baseline --steps ${STEPS:-20} --warmup 5 2>/dev/null | python -c "
+  env "$@" python bench.py --full --no-extra --no-cpu-baseline --steps ${STEPS:-20} --warmup 5 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); p=l['phases_ms']; k=l['kernels_ms']; r=l['resident_one_lane']
 h=sum(v['ms'] for n,v in k.items() if n in ('compress_layer','compress_layer_rowdig','hash_leaves','hash_rows'))

@@ -18,6 +18,6 @@ for rep in 1 2; do
   run every_wavefront ZKM_Q_UNITABLE=0
   run table ZKM_Q_UNITABLE=1
 done
-for i in 1 2; do python bench.py --no-extra --no-cpu-baseline --steps 20 --warmup 2 2>/dev/null | python -c "
+for i in 1 2; do python bench.py --full --no-extra --no-cpu-baseline --steps 20 --warmup 2 2>/dev/null | python -c "
 import json,sys
 l=json.loads(sys.stdin.read()); print('default line (table): %.3f ms/shard = %.3f shard-proofs/s, resident one lane %.3f ms' % (l['ms_per_step'], l['value'], l['resident_one_lane']['ms_per_step']))"; done

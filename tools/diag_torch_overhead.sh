@@ -7,7 +7,7 @@ variant() {   # label, python prelude
   python -c "
 $2
 import sys, runpy
-sys.argv=['bench.py','--steps','40','--warmup','3','--no-extra','--no-cpu-baseline']
+sys.argv=['bench.py','--full','--steps','40','--warmup','3','--no-extra','--no-cpu-baseline']
 runpy.run_path('bench.py', run_name='__main__')" 2>/dev/null | show "$1"
 }
 for rep in 1 2 3; do

@@ -15,10 +15,10 @@ cd /tmp && export TMPDIR=/tmp
 db() { find "$1" -name '*_results.db' | head -1; }
 QUICK=0; SYN=0
 for a in "$@"; do [ "$a" = quick ] && QUICK=1; [ "$a" = syn ] && SYN=1; done
-python $R/bench.py > $OUT/r04_fibs21_bench.json 2> $OUT/bench.err
+python $R/bench.py --full > $OUT/r04_fibs21_bench.json 2> $OUT/bench.err
 profile() {   # tag, extra bench args
   local T=$1; shift
-  local B="python $R/bench.py $* --no-cpu-baseline --no-extra"
+  local B="python $R/bench.py --full $* --no-cpu-baseline --no-extra"
   cd /tmp
   rocprofv3 --kernel-trace --stats -d $OUT/stats_$T -o stats -- $B --steps 5 --warmup 1 > $OUT/r04_${T}_bench_profiled.json 2> $OUT/stats_$T.err
   # counter passes: 1 warm-up + 1 timed proof, no per-kernel timing pass (2 proofs per run)

@@ -54,5 +54,5 @@ fi
 # roofline.traffic only from a profile whose csrc digest is the tree's
 cp $OUT/r05_fibs21_hbm_traffic.json $R/profiles/ 2>/dev/null
 cd $R
-python $R/bench.py --steps 20 --warmup 5 > $OUT/r05_fibs21_bench.json 2> $OUT/bench.err
+python $R/bench.py --full --steps 20 --warmup 5 > $OUT/r05_fibs21_bench.json 2> $OUT/bench.err
 ls -la $OUT

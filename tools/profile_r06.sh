@@ -58,7 +58,7 @@ fi
 # roofline.traffic only from a profile whose csrc digest is the tree's
 cp $OUT/r06_fibs21_hbm_traffic.json $R/profiles/ 2>/dev/null
 cd $R
-python $R/bench.py --steps 20 --warmup 5 > $OUT/r06_fibs21_bench.json 2> $OUT/bench.err
+python $R/bench.py --full --steps 20 --warmup 5 > $OUT/r06_fibs21_bench.json 2> $OUT/bench.err
 python - <<PY
 import json
 l = json.loads(open("$OUT/r06_fibs21_bench.json").read().strip().splitlines()[-1])

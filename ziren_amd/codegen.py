@@ -713,6 +713,23 @@ def _private_tmp(out: str) -> str:
     return f"{out}.{os.getpid()}.{__import__('threading').get_ident()}.tmp"
 
 
+def build_jobs() -> int:
+    """How many hipcc processes run side by side: MAX_JOBS when it is set, else the CPUs this process may run on, at most 16. Not
+    os.cpu_count(): a container sees every logical CPU of its host, and one hipcc is a tree of several processes, so a pool sized by the
+    host can exceed the container's process limit."""
+    env = os.environ.get("MAX_JOBS", "").strip()
+    if env.isdigit() and int(env) > 0:
+        return int(env)
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    return max(1, min(16, n))
+
+
+_hipcc_slots = __import__("threading").BoundedSemaphore(build_jobs())     # shared by every pool below, nested ones included
+
+
 def _compile(src: str, out: str, verbose: bool = False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     with tempfile.TemporaryDirectory() as td:
@@ -723,7 +740,8 @@ def _compile(src: str, out: str, verbose: bool = False):
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--genco", "-I", CSRC, path, "-o", tmp]
         if verbose:
             print(" ".join(cmd))
-        subprocess.check_call(cmd)
+        with _hipcc_slots:
+            subprocess.check_call(cmd)
     os.replace(tmp, out)
 
 
@@ -749,7 +767,7 @@ def specialize(program: np.ndarray, force: bool = False, verbose: bool = False) 
             sources = emit_part_sources(program)
             with tempfile.TemporaryDirectory() as td:
                 outs = [os.path.join(td, f"q_{h}_{n}.hsaco") for n in range(len(sources))]
-                with ThreadPoolExecutor(max_workers=min(len(sources), os.cpu_count() or 1)) as pool:
+                with ThreadPoolExecutor(max_workers=min(len(sources), build_jobs())) as pool:
                     list(pool.map(lambda so: _compile(so[0], so[1], verbose), zip(sources, outs)))
                 blobs = [open(o, "rb").read() for o in outs]
             blob = PARTS_MAGIC + np.array([len(blobs), 0], dtype="<u4").tobytes() + np.array([len(b) for b in blobs], dtype="<u8").tobytes()
@@ -766,7 +784,7 @@ def specialize(program: np.ndarray, force: bool = False, verbose: bool = False) 
 def specialize_many(programs, verbose: bool = False):
     """specialize() for a list of programs, compiling the missing ones side by side (the build step: every recorded chip)."""
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=os.cpu_count() or 1) as pool:
+    with ThreadPoolExecutor(max_workers=build_jobs()) as pool:
         return list(pool.map(lambda prog: specialize(prog, verbose=verbose), programs))
 
 
@@ -942,7 +960,7 @@ def specialize_perm(blob, log_quotient_degree: int, force: bool = False, verbose
 
 def specialize_perm_many(chips, verbose: bool = False):
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=os.cpu_count() or 1) as pool:
+    with ThreadPoolExecutor(max_workers=build_jobs()) as pool:
         return list(pool.map(lambda c: specialize_perm(c.lookups_blob, c.log_quotient_degree, verbose=verbose), chips))
 
 
